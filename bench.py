@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """NeMo fit benchmark: iterations/second of the per-iteration optimisation step (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Workload (config.workload): the Baseball-Pitch fit of BASELINE.json configs[1] -- 8 instances x 300
 frames, full batch N = 2400 (instance x frame) samples per step, NemoV2 with the published-run
@@ -138,6 +138,10 @@ def parse(argv=None):
     ap.add_argument('--skin-nnz', type=int, default=SKIN_NNZ,
                     help='non-zero skinning weights per vertex of the synthetic body model (4 = as the published SMPL model; 24 = dense)')
     ap.add_argument('--cpu-child', default='', help=argparse.SUPPRESS)
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='after the timed regions, write what the last timed step returned to its caller (loss scalars, info_dict '
+                         'arrays; rank 0) as DIR/<name>.npy in float32 / float64, at most 64 MB in all: larger per-sample arrays '
+                         'keep a fixed, seeded sample of rows (DIR/sample_rows.npy).  The inputs depend on the arguments only')
     return ap.parse_args(argv)
 
 
@@ -449,6 +453,49 @@ def timed(cx, fn, n):
         cx.dist.all_reduce(tmax, op=cx.dist.ReduceOp.MAX)
         dt = float(tmax)
     return dt, out
+
+
+DUMP_BUDGET = 64 << 20          # bytes of --dump-outputs in all
+
+
+def host_outputs(out):
+    """(loss_dict, info_dict) of one model.step() -> {name: host array}.  Run before the next step() call: the info_dict
+    arrays of a full-batch training step are views of buffers the next step reuses, materialised on first access.
+    Integer arrays (the sample indices) become float64 (exact), everything else float32."""
+    import numpy as np
+    ld, info = out
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in ld.items()}
+    for k in info.keys():
+        v = info[k]
+        if v is None:
+            continue
+        v = np.asarray(v.detach().cpu().numpy() if hasattr(v, 'detach') else v)
+        arrays[k] = v.astype(np.float64 if v.dtype.kind in 'iub' or v.dtype == np.float64 else np.float32)
+    return arrays
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, DUMP_BUDGET bytes in all.  Over the budget, every per-sample array (first
+    axis = the step's samples) keeps the same fixed, seeded subset of rows, whose indices go to sample_rows.npy."""
+    import numpy as np
+    n = len(arrays['view_idx']) if 'view_idx' in arrays else None
+    per_sample = [k for k, v in arrays.items() if n and v.ndim >= 1 and v.shape[0] == n]
+    total = sum(v.nbytes for v in arrays.values())
+    sampled = None
+    if total > DUMP_BUDGET and per_sample:
+        fixed = total - sum(arrays[k].nbytes for k in per_sample)
+        row = sum(arrays[k].nbytes for k in per_sample) / n + 8                  # (+ sample_rows itself, float64)
+        keep = max(1, min(n, int((DUMP_BUDGET - fixed) // row)))
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = dict(arrays, **{k: arrays[k][rows] for k in per_sample}, sample_rows=rows.astype(np.float64))
+        sampled = {'rows': keep, 'of': n, 'arrays': per_sample}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f'bench.py: --dump-outputs would write {total} bytes (> {DUMP_BUDGET})')
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), np.ascontiguousarray(v))
+    return {'dir': path, 'files': sorted(k + '.npy' for k in arrays), 'bytes': int(total), 'sampled': sampled}
 
 
 def snapshot(model):
@@ -898,6 +945,8 @@ def worker_main(opts):
     # EXACTLY --steps steps per timed region (barrier + synchronize on both sides, max over ranks); --repeat regions, the
     # median one is reported (all of them are listed in `repeat_ms_per_step`)
     regions = [timed(cx, step, opts.steps) for _ in range(max(1, opts.repeat))]
+    # (--dump-outputs: what the last timed step returned, taken before any further step reuses its buffers)
+    dump = write_outputs(opts.dump_outputs, host_outputs(regions[-1][1])) if opts.dump_outputs and rank == 0 else None
     order = sorted(range(len(regions)), key=lambda i: regions[i][0])
     elapsed, (ld, _) = regions[order[len(order) // 2]]
     repeat_ms = [round(1e3 * r[0] / opts.steps, 4) for r in regions]
@@ -1016,6 +1065,8 @@ def worker_main(opts):
             'final_total_loss': float(ld['total_loss']),
             'roofline': roof, 'cpu_baseline': cpu, 'torch_gpu_baseline': tgpu,
         }
+        if dump:
+            out['dump_outputs'] = dump
         out.update(extra)
         if opts.dtype == 'f32' and mesh_split:
             fm = extra.get('f32_mfma_blend') or {}

@@ -77,6 +77,39 @@ def test_step_flops_accounting():
     assert 120e9 < tot < 135e9
 
 
+def test_dump_outputs_format_and_budget(tmp_path):
+    """--dump-outputs: one .npy per returned array, float32 / float64 only; over 64 MB the per-sample arrays keep the SAME
+    seeded rows in every run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from nemo_cvpr2023_amd.neural_motion_model import _LazyInfo
+    n = 300000
+    g = torch.Generator().manual_seed(0)
+
+    def out():
+        info = _LazyInfo({'view_idx': torch.arange(n) % 7, 'frame_idx': torch.arange(n) // 7})
+        info.lazy.update(j=lambda: torch.randn(n, 45, 3, generator=torch.Generator().manual_seed(1)),
+                         points2d=lambda: torch.randn(n, 45, 2, generator=torch.Generator().manual_seed(2)))
+        return {'kp_loss': np.asarray(np.float32(1.5)), 'total_loss': np.asarray(np.float32(2.5))}, info
+    small = bench.write_outputs(str(tmp_path / 'small'), {'total_loss': np.asarray(np.float32(2.5)),
+                                                          'j': torch.randn(8, 3, generator=g).numpy()})
+    assert small['sampled'] is None and small['files'] == ['j.npy', 'total_loss.npy']
+    a = bench.write_outputs(str(tmp_path / 'a'), bench.host_outputs(out()))
+    b = bench.write_outputs(str(tmp_path / 'b'), bench.host_outputs(out()))
+    assert a['bytes'] <= bench.DUMP_BUDGET and a['sampled']['of'] == n and 0 < a['sampled']['rows'] < n
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in a['files']) <= bench.DUMP_BUDGET + 128 * len(a['files'])
+    assert set(a['files']) == {'kp_loss.npy', 'total_loss.npy', 'view_idx.npy', 'frame_idx.npy', 'j.npy', 'points2d.npy',
+                               'sample_rows.npy'}
+    for f in a['files']:
+        x, y = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    rows = np.load(tmp_path / 'a' / 'sample_rows.npy').astype(np.int64)
+    full = torch.randn(n, 45, 3, generator=torch.Generator().manual_seed(1)).numpy()
+    assert np.array_equal(np.load(tmp_path / 'a' / 'j.npy'), full[rows])
+    assert np.array_equal(np.load(tmp_path / 'a' / 'frame_idx.npy'), rows // 7)
+
+
 # ------------------------------------------------------------------------------------------ GPU
 def _rccl_world1(mode, q):
     import torch.distributed as dist
